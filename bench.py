@@ -18,12 +18,16 @@ the wall time of the K timed frames / K (from an empty pipeline to the last fram
 memory); device_ms_per_frame the same frames without the D2H; frame_latency_ms one frame
 rendered alone (render, [gather, unpack,] D2H, host sync), median of up to 20.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Fields beyond the
-contract: frames_in_flight, frames_per_launch, device_ms_per_frame, frame_latency_ms,
-primary_mrays_s, rays_per_frame, ms_kernels, launches (k_trace launches per region, in
-order: warmup, timed, device-only, profiled, latency — the key to the committed rocprofv3
-trace), parity, roofs (physical roofs from the committed PMC passes of this command),
-cpu_baseline.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up,
+warms up, times the K frames, traces one more frame with the device counters on (rays per
+frame, the numerator of `value`; the K frames again where the camera or the lights move),
+writes the last timed frame if --dump-outputs DIR is given, and prints the line.  --full adds
+everything else, in regions of their own after the timed one, and these fields:
+device_ms_per_frame, frame_latency_ms, primary_mrays_s, ms_kernels, roofline, launches of
+every region (k_trace launches per region, in order: warmup, timed, device-only, profiled,
+latency — the key to the committed rocprofv3 trace), parity, roofs (physical roofs from the
+committed PMC passes of this command), cpu_baseline.  The committed lines under profiles/
+are --full lines.
 """
 from __future__ import annotations
 
@@ -201,8 +205,16 @@ def parse():
                          "(environment.go:65-69): a new light-table key every frame")
     ap.add_argument("--light-deg", type=float, default=2.0, help="light orbit step per frame (degrees)")
     ap.add_argument("--no-d2h", action="store_true", help="leave the assembled frames in HBM (no host output)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline: the "
+                         "device-only, profiled and single-frame-latency regions, the roofline block, the parity "
+                         "gate against the oracle and the CPU baselines (a plain run only sets up, warms up, times "
+                         "the steps, counts one frame's rays and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed frame as the caller receives it (rgb8 and valid; float32) to "
+                         "DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baselines")
+    ap.add_argument("--no-parity", action="store_true", help="--full: without the parity gate")
     ap.add_argument("--no-prefilter", action="store_true", help="ablation: always divide for r2")
     ap.add_argument("--no-octant", action="store_true", help="ablation: generic (sorted) child-box test only")
     ap.add_argument("--reflect-chains", action="store_true",
@@ -421,6 +433,32 @@ def load_profile(path: str, shape: dict):
     return pj
 
 
+# keys of the line whose figures come from the regions only a --full run has
+FULL_ONLY_KEYS = ("device_ms_per_frame", "device_mrays_s", "frame_latency_ms", "primary_mrays_s", "ms_kernels",
+                  "roofline", "brute_force_equivalent")
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(dirname: str, rgb8: np.ndarray, valid=None) -> None:
+    """--dump-outputs DIR: the last timed frame as its caller receives it, DIR/rgb8.npy ((pixels, 3))
+    and DIR/valid.npy ((pixels,)) in float32, pixels in framebuffer order.  A frame beyond
+    DUMP_MAX_BYTES is written as a fixed sample of its pixels (numpy's default_rng(DUMP_SAMPLE_SEED),
+    the same pixels in every run of the same size), whose indices go to DIR/pixel_index.npy
+    (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    n = rgb8.shape[0]
+    per_px = 4 * (3 + (1 if valid is not None else 0))
+    if n * per_px > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (per_px + 8) - 64  # 8: the index; 64 pixels' worth for the .npy headers
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+        np.save(os.path.join(dirname, "pixel_index.npy"), idx.astype(np.float64))
+        rgb8, valid = rgb8[idx], None if valid is None else valid[idx]
+    np.save(os.path.join(dirname, "rgb8.npy"), np.ascontiguousarray(rgb8, dtype=np.float32))
+    if valid is not None:
+        np.save(os.path.join(dirname, "valid.npy"), np.ascontiguousarray(valid, dtype=np.float32))
+
+
 def box_main(a) -> None:
     """--box N: the box drop-in under the reference master's traffic.  The
     native caller worker_c/box_bench keeps --inflight frames in flight, each frame's
@@ -462,7 +500,9 @@ def box_main(a) -> None:
     }
     if timers:  # MIRT_BOX_TIMERS=1: host time per phase of an order (warmup orders included)
         line["box_timers"] = timers[-1]
-    if not a.no_parity:
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rgb8)
+    if a.full and not a.no_parity:
         from oracle.oracle import Oracle
         from oracle.scene_py import load_scene
         ref = Oracle(load_scene(a.scene), use_rtree=True).frame(W, H, nthreads=HOST_CORES)
@@ -623,11 +663,17 @@ def main():
             # the D2H'd frame (checked against the oracle below): views of the pinned planes
             # now, copied after the device-only region (which leaves host output off), so the
             # GPU does not idle through a host copy (33 MB at 4K) between the two regions
-            host_last = sh.host_frame(last, copy=False)
+            # (a plain run copies at once: its counting frame below reuses the pinned planes)
+            host_last = sh.host_frame(last, copy=not a.full)
+        dump_last = None
+        if a.dump_outputs and rank == 0 and host_last is None:
+            # outputs left in HBM: the last timed frame's planes, before a later region reuses them
+            fr = sh.frame
+            dump_last = (fr.rgb8.cpu().numpy(), fr.valid.cpu().numpy())
 
         # the same frames without the D2H (device-resident outputs)
         dev_elapsed = None
-        if d2h:
+        if a.full and d2h:
             if rank == 0:
                 sh.set_host_output(False)
             barrier()
@@ -645,18 +691,21 @@ def main():
             if rank == 0:
                 sh.set_host_output(True)
 
-        # profiled region: HIP events around every k_trace launch + device counters
+        # profiled region: HIP events around every k_trace launch + device counters.  A plain run
+        # needs only the rays per frame of `value` from it: one frame where every frame has the
+        # same inputs, the timed frames again where the camera or the lights move
+        n_prof = a.steps if (a.full or len(seq) > 1) else min(a.steps, 1)
         ctx.profile_enable(True)
-        for k in range(a.steps):
+        for k in range(n_prof):
             sh.render(frame_at(k))
         finish()
         torch.cuda.synchronize(dev)
         ctx.profile_enable(False)
-        count("profiled", a.steps)
+        count("profiled", n_prof)
 
         # single-frame latency: one frame alone (render, gather + unpack, D2H, host sync), median
         lat = []
-        for k in range(min(a.steps, 20)):
+        for k in range(min(a.steps, 20) if a.full else 0):
             barrier()
             torch.cuda.synchronize(dev)
             l0 = time.perf_counter()
@@ -664,7 +713,8 @@ def main():
             finish()
             torch.cuda.synchronize(dev)
             lat.append(time.perf_counter() - l0)
-        count("latency", min(a.steps, 20), batched=False)
+        if a.full:
+            count("latency", min(a.steps, 20), batched=False)
         latency = float(np.median(lat)) if lat else 0.0
     prof = ctx.profile_read()
 
@@ -716,7 +766,7 @@ def main():
         if a.lights != "static":
             shape["lights"] = a.lights
         build_id = rt._lib.lib().mirt_build_id().decode()
-        pj, pj_path, why_not = find_profile(a.profile_json, shape, build_id)
+        pj, pj_path, why_not = find_profile(a.profile_json, shape, build_id) if a.full else (None, None, None)
         frames_per_launch = pl / nlaunch
         dev_ms = dev_elapsed / steps * 1e3 if dev_elapsed else ms
         line = {
@@ -786,6 +836,12 @@ def main():
             "definition": "72 B x triangles x rays per frame (the work a brute-force sweep would do) / device ms "
                           "per frame: an effective rate, not a bandwidth",
             "effective_tb_s": round(bf_bytes / (dev_ms / 1e3) / 1e12, 1)}
+        if not a.full:
+            # a plain run has no device-only, profiled-steps or latency region: their figures are --full's
+            for k in FULL_ONLY_KEYS:
+                del line[k]
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, *(host_last if host_last is not None else dump_last))
         if pj:
             # physical roofs over the frame interval (counters of this exact command, profiles/)
             per_frame = lambda x: x / pj["frames_per_launch"]  # noqa: E731
@@ -803,7 +859,7 @@ def main():
                 "hbm_frac": round(per_frame(pj["hbm_bytes_per_launch"]) / iv / 1e9 / HBM_PEAK_GBS, 4),
                 "output_bytes_per_frame": W * H * 4,
             }
-        if not a.no_parity and rank == 0:
+        if a.full and not a.no_parity and rank == 0:
             if host_last is not None:
                 rgb8, valid = host_last
             else:
@@ -830,7 +886,7 @@ def main():
             line["parity"]["frame"] = "host copy (D2H)" if host_last is not None else "device framebuffer"
             line["parity"]["rgb_f64"]["frame"] = ("device fp64 rgb plane of the last timed frame's inputs, traced "
                                                   "again through the frame group with the plane on")
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.scene, W, H)
         print(json.dumps(line), flush=True)
     if world > 1:

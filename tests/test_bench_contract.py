@@ -9,7 +9,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # round 6, final build (profiles/r06i_*): every line ran after its command's profile was committed
 TAG = "r06i"
-DRIVER = f"profiles/{TAG}_bench_driver_1.log"   # python3 bench.py --gpus 1 --steps 20 --warmup 5
+# the committed lines carry everything a --full run prints (bench.py's docstring)
+DRIVER = f"profiles/{TAG}_bench_driver_1.log"   # python3 bench.py --full --gpus 1 --steps 20 --warmup 5
 PROFILED = [DRIVER] + [f"profiles/{TAG}_bench_{k}.log" for k in ("driver_2", "driver_3", "orbit", "lights", "config3",
                                                                   "config3ns", "config4", "brute")]
 UNPROFILED = [f"profiles/{TAG}_bench_{k}.log" for k in ("bench500", "orbit500")]  # 500 frames: no PMC of that shape

@@ -6,7 +6,7 @@ ARGS=$1; R=$2; shift 2
 OUT=gpurun_out/ab_bench.txt
 mkdir -p gpurun_out; : > $OUT
 for rep in $(seq 1 $R); do for L in "$@"; do
-  MIRT_LIB=distributed_raytracer_amd/$L timeout -k 10 300 python3 bench.py $ARGS --no-cpu-baseline --no-parity \
+  MIRT_LIB=distributed_raytracer_amd/$L timeout -k 10 300 python3 bench.py --full $ARGS --no-cpu-baseline --no-parity \
     > gpurun_out/ab_one.log 2>&1 || { echo "$L failed"; tail -5 gpurun_out/ab_one.log; exit 1; }
   python3 -c "
 import json; t=open('gpurun_out/ab_one.log').read(); d=json.loads(t[t.index('{'):].splitlines()[0])

@@ -16,7 +16,7 @@ for rep in $(seq 1 $R); do
       stream) L=libmirt.so; X="--lds-stream" ;;
       stream_sh) L=libmirt_ss1.so; X="--lds-stream" ;;
     esac
-    MIRT_LIB=distributed_raytracer_amd/$L timeout -k 10 300 python3 bench.py $A $X > $OUT/$v.log 2>&1 || { tail -5 $OUT/$v.log; exit 1; }
+    MIRT_LIB=distributed_raytracer_amd/$L timeout -k 10 300 python3 bench.py --full $A $X > $OUT/$v.log 2>&1 || { tail -5 $OUT/$v.log; exit 1; }
     python3 -c "
 import json; t=open('$OUT/$v.log').read(); d=json.loads(t[t.index('{\"metric'):].splitlines()[0])
 print($rep, '$v', d['ms_per_step'], d.get('device_ms_per_frame'), d.get('frame_latency_ms'), d['value'], (d.get('parity') or {}).get('bit_exact'))" >> $OUT/ab.txt

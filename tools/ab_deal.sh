@@ -13,13 +13,13 @@ print('$1', d['ms_per_step'], d.get('device_ms_per_frame'), d.get('frame_latency
 for rep in $(seq 1 $R); do
   for v in on off; do
     E=""; [ $v = off ] && E="MIRT_NO_DEAL=1"
-    env $E timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_$v.log 2>&1 || { tail -5 $OUT/bench_$v.log; exit 1; }
+    env $E timeout -k 10 200 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_$v.log 2>&1 || { tail -5 $OUT/bench_$v.log; exit 1; }
     line "bench20 $v" $OUT/bench_$v.log
   done
 done
 for v in on off; do
   E=""; [ $v = off ] && E="MIRT_NO_DEAL=1"
-  env $E timeout -k 10 200 python3 bench.py --gpus 1 --steps 300 --warmup 20 --no-cpu-baseline --no-parity > $OUT/bench300_$v.log 2>&1 || exit 1
+  env $E timeout -k 10 200 python3 bench.py --full --gpus 1 --steps 300 --warmup 20 --no-cpu-baseline --no-parity > $OUT/bench300_$v.log 2>&1 || exit 1
   line "bench300 $v" $OUT/bench300_$v.log
   for n in 8 2; do
     for fr in 20 200; do

@@ -7,7 +7,7 @@ IFS='|' read -ra VARS <<< "$SPECS"
 for v in "${VARS[@]}"; do
   label=${v%%:*}; envs=${v#*:}
   LOG=/tmp/ab_$label.log
-  env $envs timeout -k 10 150 python3 bench.py --steps "$STEPS" --warmup 5 --no-cpu-baseline --no-parity "$@" \
+  env $envs timeout -k 10 150 python3 bench.py --full --steps "$STEPS" --warmup 5 --no-cpu-baseline --no-parity "$@" \
     > "$LOG" 2>&1 || { echo "$label failed"; tail -3 "$LOG"; exit 1; }
   python3 -c "
 import json

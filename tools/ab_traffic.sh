@@ -8,7 +8,7 @@ mkdir -p $OUT
 for L in "$@"; do
   for C in FETCH_SIZE WRITE_SIZE; do
     MIRT_LIB=distributed_raytracer_amd/$L timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d $OUT/$L.$C -o run -- \
-      python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-parity ${TRAFFIC_ARGS:-} > $OUT/$L.$C.log 2>&1 || { echo "$L $C failed"; exit 1; }
+      python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-parity ${TRAFFIC_ARGS:-} > $OUT/$L.$C.log 2>&1 || { echo "$L $C failed"; exit 1; }
   done
   python3 - "$OUT" "$L" <<'PY'
 import csv, sys

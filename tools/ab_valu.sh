@@ -10,7 +10,7 @@ for V in "$@"; do
   L=${V%%@*}; X=""; [[ "$V" == *@* ]] && X=${V#*@}
   N=$L${X// /}
   MIRT_LIB=distributed_raytracer_amd/$L timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU \
-    SQ_THREAD_CYCLES_VALU --output-format csv -d $OUT/$N -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 \
+    SQ_THREAD_CYCLES_VALU --output-format csv -d $OUT/$N -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 \
     --no-cpu-baseline --no-parity $X > $OUT/$N.log 2>&1 || { echo "$N failed"; tail -5 $OUT/$N.log; exit 1; }
   python3 - "$OUT/$N" "$N" <<'PY'
 import csv, collections, json, sys

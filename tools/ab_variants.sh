@@ -16,11 +16,11 @@ for rep in $(seq 1 $R); do
   for v in $VARIANTS; do
     n=${v%%:*}; E=$(envs "$v")
     if [[ " $SECTIONS " == *" bench "* ]]; then
-      env $E timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/b_$n.log 2>&1 || { tail -5 $OUT/b_$n.log; exit 1; }
+      env $E timeout -k 10 200 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/b_$n.log 2>&1 || { tail -5 $OUT/b_$n.log; exit 1; }
       line "bench20 $n" $OUT/b_$n.log
     fi
     if [[ " $SECTIONS " == *" bench300 "* ]]; then
-      env $E timeout -k 10 200 python3 bench.py --gpus 1 --steps 300 --warmup 20 --no-cpu-baseline --no-parity > $OUT/b3_$n.log 2>&1 || { tail -5 $OUT/b3_$n.log; exit 1; }
+      env $E timeout -k 10 200 python3 bench.py --full --gpus 1 --steps 300 --warmup 20 --no-cpu-baseline --no-parity > $OUT/b3_$n.log 2>&1 || { tail -5 $OUT/b3_$n.log; exit 1; }
       line "bench300 $n" $OUT/b3_$n.log
     fi
     if [[ " $SECTIONS " == *" rehearse "* ]]; then

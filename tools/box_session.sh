@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round 6: the box drop-in on the GPU box.  Its tests, then bench.py --box lines for boxes of 1
+# Round 6: the box drop-in on the GPU box.  Its tests, then bench.py --full --box lines for boxes of 1
 # and 8 entries (device 0 repeated: copy transport) serving the master's orders for 1 and 8
 # workers, beside the frame group's driver line.   tools/box_session.sh OUTDIR
 set -u
@@ -17,7 +17,7 @@ run() {  # name timeout cmd...
 SPECS=${BOX_SPECS:-1:1:8 1:1:16 8:1:8 1:8:8 8:8:8}
 for spec in $SPECS; do
   IFS=: read -r e wk f <<< "$spec"
-  run box_e${e}_w${wk}_f${f} 300 python3 bench.py --box $e --box-workers $wk --inflight $f --steps ${BOX_STEPS:-300} --warmup 20
+  run box_e${e}_w${wk}_f${f} 300 python3 bench.py --full --box $e --box-workers $wk --inflight $f --steps ${BOX_STEPS:-300} --warmup 20
 done
-run driver 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline
+run driver 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline
 echo "box session done"

@@ -35,22 +35,22 @@ case ${1:-lines} in
   lines)  # after the profiles are committed: the lines cite them (same build id)
     step tests 900 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread
     step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()"
-    for k in 1 2 3; do step driver_$k 300 python3 bench.py --gpus 1 --steps 20 --warmup 5; done
-    step bench500 300 python3 bench.py --gpus 1 --no-cpu-baseline
-    step orbit 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --camera orbit --no-cpu-baseline
-    step lights 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --lights orbit --no-cpu-baseline
-    step orbit500 300 python3 bench.py --gpus 1 --camera orbit --no-cpu-baseline ;;
+    for k in 1 2 3; do step driver_$k 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5; done
+    step bench500 300 python3 bench.py --full --gpus 1 --no-cpu-baseline
+    step orbit 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --camera orbit --no-cpu-baseline
+    step lights 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --lights orbit --no-cpu-baseline
+    step orbit500 300 python3 bench.py --full --gpus 1 --camera orbit --no-cpu-baseline ;;
   lines_configs)
     sphere
-    step config3 600 python3 bench.py $C3
-    step config3ns 600 python3 bench.py $C3 --no-lds-stream
-    step config4 600 python3 bench.py $C4
+    step config3 600 python3 bench.py --full $C3
+    step config3ns 600 python3 bench.py --full $C3 --no-lds-stream
+    step config4 600 python3 bench.py --full $C4
     step stream_window 300 env MIRT_LIB=distributed_raytracer_amd/libmirt_diag.so python3 tools/stream_window.py /tmp/sphere1m/scene.json ;;
   box)
     for spec in 1:1:8:20 1:1:8:300 1:1:16:300 8:1:8:20 8:1:8:300 1:8:8:20 1:8:8:300; do
       IFS=: read -r e wk f st <<< "$spec"
       for rep in 1 2; do
-        step box_e${e}_w${wk}_f${f}_s${st}_$rep 300 python3 bench.py --box $e --box-workers $wk --inflight $f --steps $st --warmup 20
+        step box_e${e}_w${wk}_f${f}_s${st}_$rep 300 python3 bench.py --full --box $e --box-workers $wk --inflight $f --steps $st --warmup 20
       done
     done ;;
   rehearse)

@@ -8,6 +8,7 @@ set -u
 OUT=${1:-gpurun_out/session}; shift
 mkdir -p "$OUT"
 STEPS=${*:-"tests bench sweep profile"}
+SPHERE=$(dirname "$(mktemp -u)")/sphere1m  # the configs[3] scene that the config3 step generates
 step() {  # name timeout cmd...
   local name=$1 t=$2; shift 2
   echo "== $name: $*"
@@ -20,15 +21,15 @@ step() {  # name timeout cmd...
 for s in $STEPS; do
   case $s in
     tests) step tests 900 python3 -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"} ;;
-    bench) step bench 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 ;;
-    bench500) step bench500 300 python3 bench.py --gpus 1 --no-cpu-baseline ;;
-    orbit) step orbit 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --camera orbit --no-cpu-baseline ;;
-    orbit500) step orbit500 300 python3 bench.py --gpus 1 --camera orbit --no-cpu-baseline ;;
-    brute) step brute 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --brute-force --no-cpu-baseline ;;
+    bench) step bench 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 ;;
+    bench500) step bench500 300 python3 bench.py --full --gpus 1 --no-cpu-baseline ;;
+    orbit) step orbit 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --camera orbit --no-cpu-baseline ;;
+    orbit500) step orbit500 300 python3 bench.py --full --gpus 1 --camera orbit --no-cpu-baseline ;;
+    brute) step brute 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --brute-force --no-cpu-baseline ;;
     config3) [ -f /tmp/sphere1m/scene.json ] || python3 tools/gen_sphere_obj.py /tmp/sphere1m > /dev/null
-      step config3 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --scene /tmp/sphere1m/scene.json \
+      step config3 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --scene "$SPHERE/scene.json" \
       --width 3840 --height 2160 --no-cpu-baseline ;;
-    config4) step config4 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --width 3840 --height 2160 --bounces 4 \
+    config4) step config4 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --width 3840 --height 2160 --bounces 4 \
       --no-cpu-baseline ;;
     sweep) step sweep 900 tools/shape_sweep.sh 20 5 ;;
     profile) step profile 900 tools/profile_cmd.sh ${PROF_TAG:-r03} ;;

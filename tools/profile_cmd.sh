@@ -1,5 +1,5 @@
 #!/bin/bash
-# Profile ONE bench command exactly as given (default: the driver's round-end command) on
+# Profile ONE bench command as given plus --full (default: the driver's round-end command) on
 # the GPU box: a rocprofv3 --kernel-trace --stats pass, then one --pmc pass per counter
 # group (FETCH_SIZE and WRITE_SIZE cannot share a pass on gfx950; --pmc is never combined
 # with runtime/sys traces).  Output under gpurun_out/prof_$TAG; tools/roofline.py condenses
@@ -14,7 +14,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 run() {  # name, rocprofv3 options...
   local name=$1; shift
-  timeout -k 10 300 rocprofv3 "$@" --output-format csv -d "$OUT/$name" -o run -- python3 bench.py $ARGS \
+  timeout -k 10 300 rocprofv3 "$@" --output-format csv -d "$OUT/$name" -o run -- python3 bench.py --full $ARGS \
     > "$OUT/$name.log" 2>&1 || { echo "$name pass failed rc=$?"; tail -5 "$OUT/$name.log"; exit 1; }
   echo "$name pass ok"
 }

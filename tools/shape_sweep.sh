@@ -5,7 +5,7 @@ STEPS=${1:-20}; WARM=${2:-5}; shift 2 || true
 for fb in ${SHAPES:-2,1 2,2 4,1 4,2 4,4 8,2 8,4 8,8 16,4 16,8}; do
   F=${fb%,*}; B=${fb#*,}
   LOG=/tmp/sweep_${F}_${B}.log
-  timeout -k 10 120 python3 bench.py --steps "$STEPS" --warmup "$WARM" --inflight "$F" --batch "$B" \
+  timeout -k 10 120 python3 bench.py --full --steps "$STEPS" --warmup "$WARM" --inflight "$F" --batch "$B" \
     --no-cpu-baseline --no-parity "$@" > "$LOG" 2>&1 || { echo "F=$F B=$B failed"; tail -3 "$LOG"; exit 1; }
   python3 -c "
 import json, sys

@@ -23,7 +23,7 @@ export TMPDIR=/tmp
 for name in "$@"; do
   lib=distributed_raytracer_amd/libmirt_$name.so
   [ "$name" = base ] && lib=distributed_raytracer_amd/libmirt.so
-  B="python3 bench.py --no-cpu-baseline --no-parity"
+  B="python3 bench.py --full --no-cpu-baseline --no-parity"
   MIRT_LIB=$lib timeout -k 10 120 $B --steps 200 > "$OUT/$name.bench.log" 2>&1 || { echo "$name bench failed"; tail -3 "$OUT/$name.bench.log"; exit 1; }
   i=0
   for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_WAVES" \
