@@ -63,7 +63,7 @@ class Camera(C.Structure):
 class Frame(C.Structure):
     _fields_ = [("objects", C.POINTER(Object)), ("n_objects", C.c_uint32),
                 ("lights", C.POINTER(Light)), ("n_lights", C.c_uint32), ("camera", Camera),
-                ("max_bounces", C.c_uint32), ("reserved", C.c_uint32)]
+                ("max_bounces", C.c_uint32), ("supersample", C.c_uint32)]
 
 
 class Tile(C.Structure):
@@ -162,6 +162,8 @@ SIGNATURES = {
     "mirt_debug_light_table_gpu": (C.c_int, [_P, _P, C.c_uint32, C.c_double, _P, _P, C.c_uint32, _P]),
     "mirt_set_light_cache": (C.c_int, [_P, C.c_uint64]),
     "mirt_light_cache_stats": (C.c_int, [_P, _P]),
+    "mirt_set_supersample_scratch": (C.c_int, [_P, C.c_uint64]),
+    "mirt_plan_supersample_bands": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, _P, C.c_uint32]),
     "mirt_face_bounds": (None, [_P, _P, _P, _P]),
     "mirt_object_bounds": (None, [_P, C.c_uint32, _P, _P]),
     "mirt_unpack_tiles_at_async": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P]),
@@ -188,6 +190,7 @@ SIGNATURES = {
     "mirt_box_transport": (C.c_int, [_P]),
     "mirt_box_set_strip": (C.c_int, [_P, C.c_uint32]),
     "mirt_box_set_options": (C.c_int, [_P, C.c_uint32]),
+    "mirt_box_set_supersample_scratch": (C.c_int, [_P, C.c_uint64]),
     "mirt_box_mesh_upload": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32,
                                        C.POINTER(Material), C.c_uint32, C.POINTER(C.c_uint32)]),
     "mirt_box_mesh_release": (C.c_int, [_P, C.c_uint32]),

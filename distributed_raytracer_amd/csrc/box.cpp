@@ -421,7 +421,8 @@ int box_trace(mirt_box* b, const mirt_frame* f, uint32_t x, uint32_t y, uint32_t
     }
     if (st) {
         memset(st, 0, sizeof(*st));
-        st->primary_rays = (uint64_t)w * h;
+        const uint64_t ss = std::max<uint32_t>(f->supersample, 1);  // a supersampled order counts samples
+        st->primary_rays = (uint64_t)w * h * ss * ss;
         for (uint32_t d = 0; d < active; ++d) {
             const cnt_t* s = k->sum + (size_t)d * kStatN;
             st->hits += s[kStatHits];
@@ -526,6 +527,15 @@ int mirt_box_set_options(mirt_box* b, uint32_t flags) {
     if (!b) return set_error(MIRT_E_INVALID, "NULL box");
     for (mirt_ctx* c : b->ctx) {
         int r = mirt_set_options(c, flags);
+        if (r != MIRT_OK) return r;
+    }
+    return MIRT_OK;
+}
+
+int mirt_box_set_supersample_scratch(mirt_box* b, uint64_t bytes) {
+    if (!b) return set_error(MIRT_E_INVALID, "NULL box");
+    for (mirt_ctx* c : b->ctx) {
+        int r = mirt_set_supersample_scratch(c, bytes);
         if (r != MIRT_OK) return r;
     }
     return MIRT_OK;

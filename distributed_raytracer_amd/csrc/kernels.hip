@@ -3907,6 +3907,122 @@ hipError_t launch_fill_planes(const FillJobs& jobs, uint32_t nframes, uint64_t m
     return hipGetLastError();
 }
 
+// Supersample resolve (mirt_frame.supersample = S): output pixel (i, j) of a
+// band is the mean of the S x S samples (S i + a, S j + b) of the band's traced tile, added in
+// (a outer, b inner) order from +0.0 and divided once by S * S; a sample that missed counts as
+// colour zero.  valid: any sample valid; face / object: the first valid sample's.  Consecutive
+// lanes take consecutive rows j of an output column, so for each a a wave reads one contiguous
+// run of 64 S samples of a sample column (both planes are column-major); a lane's S samples are
+// S * 24 contiguous bytes, 16-byte aligned when S is even (in_off is a multiple of S * S), and
+// are read with 16-byte loads then, with 8-byte loads for odd S.  Grid: x over 256-pixel chunks
+// of a band, y over the launch's bands.  No atomics: a pixel is one lane's.
+template <int S>
+__device__ __forceinline__ void resolve_load(const ResolveArgs& ra, uint64_t k, double (&c)[3 * S], uint8_t (&v)[S]) {
+    if constexpr (S % 2 == 0) {
+        const double2* q = (const double2*)(ra.rgb + 3 * k);
+#pragma unroll
+        for (int u = 0; u < 3 * S / 2; ++u) {
+            const double2 d = q[u];
+            c[2 * u] = d.x;
+            c[2 * u + 1] = d.y;
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < 3 * S; ++u) c[u] = ra.rgb[3 * k + u];
+    }
+    if constexpr (S % 4 == 0) {
+#pragma unroll
+        for (int u = 0; u < S / 4; ++u) {
+            const uint32_t w = ((const uint32_t*)(ra.valid + k))[u];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) v[4 * u + b] = (uint8_t)(w >> (8 * b));
+        }
+    } else if constexpr (S % 2 == 0) {
+#pragma unroll
+        for (int u = 0; u < S / 2; ++u) {
+            const uint16_t w = ((const uint16_t*)(ra.valid + k))[u];
+            v[2 * u] = (uint8_t)w;
+            v[2 * u + 1] = (uint8_t)(w >> 8);
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < S; ++u) v[u] = ra.valid[k + u];
+    }
+}
+template <int S>
+__global__ __launch_bounds__(256) void k_resolve(const ResolveArgs ra) {
+    if (ra.sum_in && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < kStatN) {
+        const cnt_t t = (ra.sum_first ? 0ull : ra.sum_acc[threadIdx.x]) + ra.sum_in[threadIdx.x];
+        ra.sum_acc[threadIdx.x] = t;
+        if (ra.sum_last) ra.sum_in[threadIdx.x] = t;
+    }
+    const ResolveBand bd = ra.band[blockIdx.y];
+    const uint64_t n = (uint64_t)bd.w * bd.h;
+    const uint64_t sh = (uint64_t)S * bd.h;  // height of a sample column
+    for (uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (uint64_t)gridDim.x * 256) {
+        const uint32_t i = (uint32_t)(p / bd.h), j = (uint32_t)(p - (uint64_t)i * bd.h);
+        double ar = 0.0, ag = 0.0, ab = 0.0;
+        bool any = false;
+        uint64_t first = 0;  // the first valid sample
+        // S <= 3: every sample column's loads in flight at once; above, one column (up to 24
+        // doubles) at a time: no instantiation spills or needs more than 84 VGPRs
+        constexpr int kColumns = S <= 3 ? S : 1;
+#pragma unroll kColumns
+        for (int a = 0; a < S; ++a) {
+            const uint64_t k = bd.in_off + ((uint64_t)S * i + a) * sh + (uint64_t)S * j;
+            double c[3 * S];
+            uint8_t v[S];
+            resolve_load<S>(ra, k, c, v);
+#pragma unroll
+            for (int b = 0; b < S; ++b) {
+                const bool ok = v[b] != 0;
+                ar = ar + (ok ? c[3 * b] : 0.0);
+                ag = ag + (ok ? c[3 * b + 1] : 0.0);
+                ab = ab + (ok ? c[3 * b + 2] : 0.0);
+                if (ok && !any) first = k + b;
+                any = any || ok;
+            }
+        }
+        const double d = (double)(S * S);
+        const double r = ar / d, g = ag / d, bl = ab / d;
+        const uint64_t q = bd.out_off + p;
+        const OutPlanes& out = ra.out;
+        if (out.rgb) {
+            out.rgb[3 * q] = r;
+            out.rgb[3 * q + 1] = g;
+            out.rgb[3 * q + 2] = bl;
+        }
+        const uint32_t r8 = c_u8(r), g8 = c_u8(g), b8 = c_u8(bl);
+        if (out.rgb8) {
+            out.rgb8[3 * q] = (uint8_t)r8;
+            out.rgb8[3 * q + 1] = (uint8_t)g8;
+            out.rgb8[3 * q + 2] = (uint8_t)b8;
+        }
+        if (out.valid) out.valid[q] = any ? 1 : 0;
+        if (out.rgbv) out.rgbv[q] = r8 | (g8 << 8) | (b8 << 16) | ((any ? 1u : 0u) << 24);
+        if (out.face) out.face[q] = any ? ra.face[first] : -1;
+        if (out.object) out.object[q] = any ? ra.object[first] : -1;
+    }
+}
+
+hipError_t launch_resolve(const ResolveArgs& ra, uint32_t s, hipStream_t stream) {
+    if (ra.nbands == 0 || ra.nbands > (uint32_t)kResolveBands) return hipErrorInvalidValue;
+    uint64_t max_px = 0;
+    for (uint32_t k = 0; k < ra.nbands; ++k) max_px = std::max<uint64_t>(max_px, (uint64_t)ra.band[k].w * ra.band[k].h);
+    const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((max_px + 255) / 256, 1u << 20)), ra.nbands);
+    switch (s) {
+#define K_RESOLVE(S)                                                             \
+    case S:                                                                      \
+        hipLaunchKernelGGL(k_resolve<S>, grid, dim3(256), 0, stream, ra);        \
+        break;
+        K_RESOLVE(2) K_RESOLVE(3) K_RESOLVE(4) K_RESOLVE(5) K_RESOLVE(6) K_RESOLVE(7) K_RESOLVE(8)
+#undef K_RESOLVE
+        default:
+            return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 // One light table, one thread per (light, triangle) record, on the stream of
 // the first frame that reads it (mirt.cpp lt_launch): lighttab.hpp's arithmetic, the host
 // builder's bits.

@@ -168,7 +168,15 @@ struct Slot {
     // device-side outputs for the host-buffer API
     void* out_buf = nullptr;
     size_t out_cap = 0;
+    // supersampled calls (mirt_frame.supersample > 1): the samples of the bands in flight
+    // (bytes) and the call's running statistic totals (kStatN, k_resolve)
+    uint8_t* ss_buf = nullptr;
+    size_t ss_cap = 0;
+    cnt_t* ss_sum = nullptr;
+    size_t ss_sum_cap = 0;
 };
+
+constexpr uint32_t kMaxSupersample = 8;
 
 struct ProfRec {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -185,6 +193,7 @@ struct mirt_ctx {
     // lists launch fewer, fuller workgroups so frames in flight can share the chip)
     uint32_t min_blocks_per_wg = 32;
     uint32_t max_workgroups = 0;  // 0: two per CU
+    uint64_t ss_scratch = (uint64_t)256 << 20;  // mirt_set_supersample_scratch: sample bytes per call
     std::mutex mu;
     std::vector<MeshDev> meshes;
     std::vector<std::unique_ptr<Slot>> slots;
@@ -288,7 +297,7 @@ void slot_free(Slot* s) {
         if (p) (void)hipFree(p);
     for (void* p : {(void*)s->hits, (void*)s->litw, (void*)s->blkdone, (void*)s->hmask, (void*)s->dir0, (void*)s->ph0, (void*)s->refl,
                     (void*)s->cost, (void*)s->counters, (void*)s->d_tiles, (void*)s->d_blocks, (void*)s->summary, s->out_buf,
-                    (void*)s->views, (void*)s->view_heads})
+                    (void*)s->views, (void*)s->view_heads, (void*)s->ss_buf, (void*)s->ss_sum})
         if (p) (void)hipFree(p);
     if (s->h_blocks) (void)hipHostFree(s->h_blocks);
     if (s->h_tiles) (void)hipHostFree(s->h_tiles);
@@ -431,6 +440,8 @@ int check_frame(const mirt_ctx* c, const mirt_frame* f) {
     if (f->n_lights && !f->lights) return fail(MIRT_E_INVALID, "lights is NULL");
     if (f->max_bounces > MIRT_MAX_BOUNCES)
         return fail(MIRT_E_LIMIT, "max_bounces > MIRT_MAX_BOUNCES (" + std::to_string(MIRT_MAX_BOUNCES) + ")");
+    if (f->supersample > kMaxSupersample)
+        return fail(MIRT_E_INVALID, "supersample > " + std::to_string(kMaxSupersample));
     for (uint32_t i = 0; i < f->n_objects; ++i) {
         uint32_t id = f->objects[i].mesh_id;
         if (id >= c->meshes.size() || !c->meshes[id].live)
@@ -1000,10 +1011,130 @@ int launch_frames(mirt_ctx* c, Slot* sl, uint32_t nf, uint32_t W, uint32_t H, co
                   uint32_t bounces, hipStream_t s, const volatile int* cancel, uint32_t max_wg_now = 0,
                   const FusedCopy* fcopy = nullptr);
 
+// Supersampling (mirt_frame.supersample = s > 1).  The bands of a tile list:
+// a tile whose s * s * w * h samples (25 bytes each, 33 with face / object) fit the cap is one
+// band, a larger one is cut into full-height ranges of cap / (bytes of one output column)
+// columns, at least one.  Returns the count; writes at most cap_out bands.
+constexpr uint64_t ss_sample_bytes(bool with_ids) { return with_ids ? 33 : 25; }
+uint64_t plan_bands(const mirt_tile* tiles, uint32_t n, uint32_t ss, bool with_ids, uint64_t cap, mirt_tile* out,
+                    uint64_t cap_out) {
+    uint64_t nb = 0;
+    for (uint32_t t = 0; t < n; ++t) {
+        const mirt_tile& tl = tiles[t];
+        const uint64_t col = (uint64_t)ss * ss * tl.h * ss_sample_bytes(with_ids);
+        const uint32_t wb = (uint32_t)std::min<uint64_t>(tl.w, std::max<uint64_t>(1, cap / col));
+        for (uint32_t x = 0; x < tl.w; x += wb, ++nb)
+            if (out && nb < cap_out) out[nb] = mirt_tile{tl.x + x, tl.y, std::min(wb, tl.w - x), tl.h};
+    }
+    return nb;
+}
+
+int enqueue_trace(mirt_ctx* c, Slot* sl, const mirt_frame* f, uint32_t W, uint32_t H, const mirt_tile* tiles,
+                  uint32_t n, const OutPlanes& out, hipStream_t s, const volatile int* cancel, uint64_t* pixels_out,
+                  uint64_t* tris_out);
+
+// A supersampled tile list: consecutive bands whose samples fit the cap together are traced by
+// one launch of the frame kernels, as the tiles (s x, s y, s w, s h) of an s W x s H screen,
+// into the slot's scratch (column-major per band, bands back to back) and resolved into the
+// caller's planes (k_resolve).  A call of several launches waits for each before it stages the
+// next: the slot's pinned block table is rewritten per launch.
+int enqueue_supersampled(mirt_ctx* c, Slot* sl, const mirt_frame* f, uint32_t W, uint32_t H, const mirt_tile* tiles,
+                         uint32_t n, const OutPlanes& out, hipStream_t s, const volatile int* cancel,
+                         uint64_t* pixels_out, uint64_t* tris_out) {
+    const uint32_t ss = f->supersample;
+    uint64_t pixels = 0;
+    int r = check_tiles(W, H, tiles, n, pixels);
+    if (r != MIRT_OK) return r;
+    if ((uint64_t)ss * W > 65535 || (uint64_t)ss * H > 65535)
+        return fail(MIRT_E_LIMIT, "supersampled screen width/height above 65535");
+    if (pixels * ss * ss > 0xffffffffull) return fail(MIRT_E_LIMIT, "more than 2^32 samples in one call");
+    const bool ids = out.face || out.object;
+    const uint64_t sb = ss_sample_bytes(ids);
+    uint64_t cap;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        cap = c->ss_scratch;
+    }
+    std::vector<mirt_tile> bands(plan_bands(tiles, n, ss, ids, cap, nullptr, 0));
+    plan_bands(tiles, n, ss, ids, cap, bands.data(), bands.size());
+    auto samples = [&](const mirt_tile& b) { return (uint64_t)ss * ss * b.w * b.h; };
+    // the launches: [first, last) runs of bands within the cap (a lone band may exceed it)
+    std::vector<size_t> cut{0};
+    uint64_t most = 0;
+    for (size_t k = 0, acc = 0; k < bands.size(); ++k) {
+        if (k > cut.back() && (acc + samples(bands[k])) * sb > cap) {
+            cut.push_back(k);
+            acc = 0;
+        }
+        acc += samples(bands[k]);
+        most = std::max<uint64_t>(most, acc);
+    }
+    cut.push_back(bands.size());
+    if ((r = dev_grow(sl->ss_buf, sl->ss_cap, (size_t)(most * sb))) != MIRT_OK) return r;
+    if ((r = dev_grow(sl->ss_sum, sl->ss_sum_cap, (size_t)kStatN)) != MIRT_OK) return r;
+    mirt_frame f1 = *f;
+    f1.supersample = 0;
+    std::vector<mirt_tile> hi;
+    uint64_t out_off = 0, tris = 0;
+    for (size_t g = 0; g + 1 < cut.size(); ++g) {
+        if (g > 0) {
+            HIP_TRY(hipStreamSynchronize(s));
+            if (cancel && *cancel) return fail(MIRT_E_CANCELLED, "cancelled");
+        }
+        hi.clear();
+        uint64_t ns = 0;
+        for (size_t k = cut[g]; k < cut[g + 1]; ++k) {
+            hi.push_back(mirt_tile{ss * bands[k].x, ss * bands[k].y, ss * bands[k].w, ss * bands[k].h});
+            ns += samples(bands[k]);
+        }
+        // scratch planes of this launch's ns samples (a multiple of s * s): rgb, face, object, valid
+        OutPlanes sp{};
+        sp.rgb = (double*)sl->ss_buf;
+        sp.face = ids ? (int32_t*)(sl->ss_buf + 24 * ns) : nullptr;
+        sp.object = ids ? (int32_t*)(sl->ss_buf + 28 * ns) : nullptr;
+        sp.valid = sl->ss_buf + (ids ? 32 : 24) * ns;
+        uint64_t px = 0;
+        if ((r = enqueue_trace(c, sl, &f1, ss * W, ss * H, hi.data(), (uint32_t)hi.size(), sp, s, cancel, &px,
+                               &tris)) != MIRT_OK)
+            return r;
+        uint64_t in_off = 0;
+        for (size_t k0 = cut[g]; k0 < cut[g + 1]; k0 += kResolveBands) {
+            ResolveArgs ra{};
+            ra.rgb = sp.rgb;
+            ra.valid = sp.valid;
+            ra.face = sp.face;
+            ra.object = sp.object;
+            ra.out = out;
+            if (k0 == cut[g]) {  // once per launch: its statistic totals
+                ra.sum_in = sl->summary;
+                ra.sum_acc = sl->ss_sum;
+                ra.sum_first = g == 0;
+                ra.sum_last = g + 2 == cut.size();
+            }
+            const size_t k1 = std::min(k0 + kResolveBands, cut[g + 1]);
+            for (size_t k = k0; k < k1; ++k) {
+                ra.band[ra.nbands++] = ResolveBand{bands[k].w, bands[k].h, in_off, out_off};
+                in_off += samples(bands[k]);
+                out_off += (uint64_t)bands[k].w * bands[k].h;
+            }
+            HIP_TRY(launch_resolve(ra, ss, s));
+        }
+    }
+    if (!sl->dedicated) {
+        HIP_TRY(hipEventRecord(sl->done, s));
+        sl->pending = true;
+    }
+    *pixels_out = pixels * ss * ss;
+    *tris_out = tris;
+    return MIRT_OK;
+}
+
 // Enqueue primary -> shadow -> shade for a tile list on stream s.
 int enqueue_trace(mirt_ctx* c, Slot* sl, const mirt_frame* f, uint32_t W, uint32_t H, const mirt_tile* tiles,
                   uint32_t n, const OutPlanes& out, hipStream_t s, const volatile int* cancel, uint64_t* pixels_out,
                   uint64_t* tris_out) {
+    if (f->supersample > 1)
+        return enqueue_supersampled(c, sl, f, W, H, tiles, n, out, s, cancel, pixels_out, tris_out);
     uint64_t pixels = 0, tris = 0;
     int r = check_tiles(W, H, tiles, n, pixels);
     if (r != MIRT_OK) return r;
@@ -1623,6 +1754,26 @@ int mirt_set_light_cache(mirt_ctx* c, uint64_t max_bytes) {
         (void)lt_reap(c, 0);
     }
     return MIRT_OK;
+}
+
+int mirt_set_supersample_scratch(mirt_ctx* c, uint64_t bytes) {
+    if (!c) return fail(MIRT_E_INVALID, "NULL context");
+    if (bytes == 0) return fail(MIRT_E_INVALID, "supersample scratch of 0 bytes");
+    std::lock_guard<std::mutex> g(c->mu);
+    c->ss_scratch = bytes;
+    return MIRT_OK;
+}
+
+int mirt_plan_supersample_bands(const mirt_tile* tiles, uint32_t n, uint32_t s, int with_ids, uint64_t cap_bytes,
+                                mirt_tile* out, uint32_t cap_out) {
+    if (!tiles || n == 0) return fail(MIRT_E_INVALID, "empty tile list");
+    if (s < 1 || s > kMaxSupersample) return fail(MIRT_E_INVALID, "supersample must be 1.." + std::to_string(kMaxSupersample));
+    if (cap_bytes == 0) return fail(MIRT_E_INVALID, "supersample scratch of 0 bytes");
+    for (uint32_t t = 0; t < n; ++t)
+        if (tiles[t].w == 0 || tiles[t].h == 0) return fail(MIRT_E_INVALID, "tile " + std::to_string(t) + " is empty");
+    const uint64_t nb = plan_bands(tiles, n, s, with_ids != 0, cap_bytes, out, cap_out);
+    if (nb > 0x7fffffffull) return fail(MIRT_E_LIMIT, "more than 2^31 bands");
+    return (int)nb;
 }
 
 int mirt_light_cache_stats(mirt_ctx* c, uint64_t out[8]) {
@@ -3444,6 +3595,8 @@ int mirt_trace_frame(mirt_group* g, const mirt_frame* f, uint64_t* index) {
     HIP_TRY(hipSetDevice(c->device));
     int r = check_frame(c, f);
     if (r != MIRT_OK) return r;
+    if (f->supersample > 1)
+        return fail(MIRT_E_INVALID, "frame groups do not supersample: mirt_frame.supersample must be 0 or 1 here");
     const uint32_t j = (uint32_t)(g->k % g->F);
     FrameRec rec{};
     uint64_t tris = 0;
@@ -3583,12 +3736,21 @@ int frame_hit_rect(mirt_ctx* c, const mirt_frame* f, uint32_t W, uint32_t H, uin
     if (r != MIRT_OK) return r;
     std::unique_ptr<FrameRec> rec(new FrameRec());
     uint64_t tris = 0;
+    // a supersampled frame: the rectangle of its samples' s W x s H screen, widened to whole
+    // output pixels (a pixel whose centre ray misses may own an off-centre sample that hits)
+    const uint32_t ss = std::max<uint32_t>(f->supersample, 1);
+    if (ss > 1 && ((uint64_t)ss * W > 65535 || (uint64_t)ss * H > 65535))
+        return fail(MIRT_E_LIMIT, "supersampled screen width/height above 65535");
     {
         std::lock_guard<std::mutex> g(c->mu);  // the mesh table
-        fill_args(c, f, W, H, rec->fa, tris);
+        fill_args(c, f, ss * W, ss * H, rec->fa, tris);
         frustum_args(c, f, rec->fa, rec->fr, rec->ocert);
     }
-    hit_rect(*rec, W, H, out);
+    hit_rect(*rec, ss * W, ss * H, out);
+    out[0] /= ss;
+    out[1] /= ss;
+    out[2] = (out[2] + ss - 1) / ss;
+    out[3] = (out[3] + ss - 1) / ss;
     return MIRT_OK;
 }
 

@@ -529,6 +529,32 @@ struct FillJobs {
     uint8_t value[kMaxFrames][kFillPlanes];
 };
 hipError_t launch_fill_planes(const FillJobs& jobs, uint32_t nframes, uint64_t max_bytes, hipStream_t s);
+
+// Supersampling (mirt_frame.supersample = s > 1): k_resolve reduces the s x s
+// samples of every output pixel of up to kResolveBands bands to the caller's planes.  A band
+// is w x h output pixels, column-major at pixel out_off of the caller's planes; its samples
+// are the s w x s h tile the frame kernels traced, column-major at sample in_off of the
+// scratch planes (in_off is a multiple of s * s).  The launch that carries sum_in also folds
+// the trace launch's statistic totals into sum_acc (sum_first: starts it) and, when sum_last
+// is set, writes the call's totals back to sum_in, where the callers read them.
+constexpr int kResolveBands = 16;
+struct ResolveBand {
+    uint32_t w, h;
+    uint64_t in_off, out_off;
+};
+struct ResolveArgs {
+    const double* rgb;      // scratch planes: samples
+    const uint8_t* valid;
+    const int32_t* face;    // null unless the caller asked for face or object
+    const int32_t* object;
+    OutPlanes out;          // the caller's planes (null: not produced)
+    cnt_t* sum_in;
+    cnt_t* sum_acc;
+    uint32_t sum_first, sum_last;
+    uint32_t nbands;
+    ResolveBand band[kResolveBands];
+};
+hipError_t launch_resolve(const ResolveArgs& ra, uint32_t s, hipStream_t stream);
 hipError_t launch_copy_rect_host(const HostCopyJobs& jobs, uint32_t nframes, uint32_t H, uint32_t max_cols,
                                  hipStream_t s);
 hipError_t launch_pack_rect(const TileDesc* tiles, uint32_t ntiles, const RectJobs& jobs, uint32_t nframes,

@@ -20,6 +20,7 @@ MIRT_E_CAMERA, a cancelled BulkTrace to MIRT_E_CANCELLED).
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import threading
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -155,6 +156,11 @@ class Context:
     def set_light_cache(self, max_bytes: int) -> None:
         L.check(L.lib().mirt_set_light_cache(self.handle, int(max_bytes)))
 
+    def set_supersample_scratch(self, max_bytes: int) -> None:
+        """Sample bytes a supersampled call holds at once (mirt.h mirt_set_supersample_scratch);
+        results never change."""
+        L.check(L.lib().mirt_set_supersample_scratch(self.handle, int(max_bytes)))
+
     def debug_box_intersect(self, origins, dirs, boxes) -> np.ndarray:
         """box.go:29-68 Box.Intersect as the kernels evaluate it (mirt_debug_fp64 op 4):
         ray i (origins[i], dirs[i]) against box i ({MinCorner, MaxCorner}, 6 doubles)."""
@@ -234,6 +240,10 @@ class Box:
     def set_options(self, flags: int) -> None:
         L.check(L.lib().mirt_box_set_options(self.box_handle, flags))
 
+    def set_supersample_scratch(self, max_bytes: int) -> None:
+        """Context.set_supersample_scratch on every entry of the box."""
+        L.check(L.lib().mirt_box_set_supersample_scratch(self.box_handle, int(max_bytes)))
+
     @property
     def transport(self) -> int:
         return int(L.lib().mirt_box_transport(self.box_handle))
@@ -301,6 +311,7 @@ class EnvMutables:
     lights: List[Light] = field(default_factory=list)
     cam: Optional[Camera] = None
     max_bounces: int = 0  # configs[4] reflection EXTENSION (mirt.h); 0 = the reference
+    supersample: int = 1  # s x s samples per pixel, EXTENSION (mirt.h); 1 = the reference
 
     def to_frame(self) -> Tuple[L.Frame, list]:
         """C mirt_frame; the second value keeps the arrays alive for the call."""
@@ -312,7 +323,8 @@ class EnvMutables:
         lts = (L.Light * max(1, len(self.lights)))()
         for i, lt in enumerate(self.lights):
             lts[i] = L.Light(_d3(lt.pos), _d3(lt.col))
-        fr = L.Frame(objs, len(self.objects), lts, len(self.lights), self.cam.to_c(), int(self.max_bounces), 0)
+        fr = L.Frame(objs, len(self.objects), lts, len(self.lights), self.cam.to_c(), int(self.max_bounces),
+                     int(self.supersample))
         return fr, [objs, lts]
 
 
@@ -529,8 +541,12 @@ class Framebuffer:
         return self.rgb8.reshape(self.width, self.height, 3).transpose(1, 0, 2)
 
 
-def draw(env: Environment, width: int, height: int, mut: Optional[EnvMutables] = None) -> Framebuffer:
-    """worker/sequential/main.go:15-32 draw: every pixel of the screen, one GPU call."""
+def draw(env: Environment, width: int, height: int, mut: Optional[EnvMutables] = None,
+         supersample: Optional[int] = None) -> Framebuffer:
+    """worker/sequential/main.go:15-32 draw: every pixel of the screen, one GPU call.
+    supersample (None: the mutables' own): s x s samples per pixel (mirt.h mirt_frame)."""
+    if supersample is not None:
+        mut = dataclasses.replace(mut or env.mutable(), supersample=int(supersample))
     r = trace_tile(env, 0, 0, width, height, width, height, mut)
     return Framebuffer(width, height, r.rgb, r.rgb8, r.valid, r.face, r.obj, r.stats)
 
@@ -557,13 +573,18 @@ class TraceResults:
 class Tracer:
     """worker/distributed Tracer: serves BulkTrace / Heartbeat for one registered scene."""
 
-    def __init__(self, scene: Environment, screen_width: int, screen_height: int):
+    def __init__(self, scene: Environment, screen_width: int, screen_height: int, supersample: int = 1):
         self.scene = scene
         self.screen_width = screen_width
         self.screen_height = screen_height
+        # s x s samples per pixel of every order (mirt.h mirt_frame.supersample): the master
+        # orders and receives the same pixels, the wire does not change
+        self.supersample = int(supersample)
 
     def bulk_trace(self, req: WorkOrder, cancel: Optional[C.c_int] = None) -> TraceResults:
         diff = self.scene.link_gob(req.diff) if isinstance(req.diff, (bytes, bytearray)) else req.diff
+        if self.supersample != 1:
+            diff = dataclasses.replace(diff or self.scene.mutable(), supersample=self.supersample)
         r = trace_tile(self.scene, req.x, req.y, req.width, req.height, self.screen_width, self.screen_height,
                        diff, cancel)
         return TraceResults(r.rgb8)

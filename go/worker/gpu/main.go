@@ -3,7 +3,10 @@
 // loop of BulkTrace (main.go:67-89) replaced by one libmirt call (package gpu).  The master,
 // the pool and the registrar see an ordinary worker (shared/comms/comms.proto:20-47).
 //
-//   gpu <master address:port> <work order port> [GPU index | all | i,j,...]
+//   gpu [-supersample N] <master address:port> <work order port> [GPU index | all | i,j,...]
+//
+// With -supersample N every order's pixels are the mean of N x N samples (mirt.h
+// mirt_frame.supersample); the master orders and receives the same pixels.
 //
 // With "all" (or a list of indices) ONE worker serves every order on several GPUs of the box
 // (gpu.NewBox: the order is cut into 8-px column strips dealt over the GPUs and assembled
@@ -17,11 +20,11 @@ import (
 	"bytes"
 	"context"
 	"encoding/gob"
+	"flag"
 	"fmt"
 	"log"
 	"net"
 	"errors"
-	"os"
 	"strconv"
 	"strings"
 	"time"
@@ -131,21 +134,26 @@ func register(registerAddr string, listenPort uint32, w *gpu.Worker) (Tracer, er
 }
 
 func main() {
-	if len(os.Args) != 3 && len(os.Args) != 4 {
+	// -supersample N (before the positional parameters): N x N samples per pixel of every order
+	supersample := flag.Uint("supersample", 1, "samples per pixel and axis (1..8); the master is unchanged")
+	flag.Parse()
+	args := flag.Args()
+	if (len(args) != 2 && len(args) != 3) || *supersample > 8 {
 		log.Fatalln("Improper parameters.  This program requires the parameters:" +
+			"\n\t(0) optional: -supersample N (1..8, default 1)" +
 			"\n\t(1) master address (including port)" +
 			"\n\t(2) work order listening port" +
 			"\n\t(3) optional: GPU index (default 0), \"all\", or a comma-separated list of GPU indices")
 	}
-	masterAddr := os.Args[1]
-	orderPort, err := strconv.ParseUint(os.Args[2], 10, 32)
+	masterAddr := args[0]
+	orderPort, err := strconv.ParseUint(args[1], 10, 32)
 	if err != nil {
-		log.Fatalf("Could not parse port number \"%s\": %v.\n", os.Args[2], err)
+		log.Fatalf("Could not parse port number \"%s\": %v.\n", args[1], err)
 	}
 	devices := []int{0}
-	if len(os.Args) == 4 {
+	if len(args) == 3 {
 		devices = nil
-		if os.Args[3] == "all" {
+		if args[2] == "all" {
 			for d := 0; d < gpu.DeviceCount(); d++ {
 				devices = append(devices, d)
 			}
@@ -153,7 +161,7 @@ func main() {
 				log.Fatalln("No GPU is visible.")
 			}
 		} else {
-			for _, f := range strings.Split(os.Args[3], ",") {
+			for _, f := range strings.Split(args[2], ",") {
 				d, err := strconv.Atoi(f)
 				if err != nil {
 					log.Fatalf("Could not parse GPU index \"%s\": %v.\n", f, err)
@@ -185,6 +193,7 @@ func main() {
 		time.Sleep(time.Millisecond * time.Duration(registerFrequency))
 	}
 	defer w.Close()
+	w.Supersample = *supersample
 
 	for {
 		// a failed registration costs one RPC; only a successful one uploads meshes

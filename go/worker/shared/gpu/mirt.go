@@ -37,6 +37,10 @@ type Worker struct {
 	ctx    *C.mirt_ctx
 	box    *C.mirt_box
 	meshes map[string]C.uint32_t // model path -> GPU mesh id
+	// Supersample is mirt_frame.supersample of every work order: s x s samples per pixel,
+	// 0 or 1 = the reference's one ray per pixel (a libmirt extension; the orders and the
+	// results keep their sizes, so the master is unchanged).
+	Supersample uint
 }
 
 // Error is a failed libmirt call: the entry, its MIRT_E_* code and mirt_last_error().
@@ -219,6 +223,7 @@ func (w *Worker) frame(scene state.Environment, env *state.EnvMutables) (fr *C.m
 	fr.camera.fov = C.double(cam.Fov)
 	fr.camera.proj_half_width = C.double(math.Tan(cam.Fov / 2.0))
 	fr.max_bounces = 0 // the reference's Trace (reflections are a libmirt extension)
+	fr.supersample = C.uint32_t(w.Supersample)
 	free = func() {
 		C.free(unsafe.Pointer(cobj))
 		C.free(unsafe.Pointer(clights))

@@ -100,7 +100,21 @@ typedef struct {
      * 0..MIRT_MAX_BOUNCES.  0 = the reference's Trace.  Semantics in DESIGN.md §4.6:
      * c = c_add(phong, c_mul(Ks, c_reflected)), R = D - 2(D.N)N, origin hit + R*1e-4. */
     uint32_t max_bounces;
-    uint32_t reserved;
+    /* Supersampled anti-aliasing EXTENSION (not in the reference; was `reserved`, which every
+     * caller zeroed): 0 and 1 trace one ray through each pixel centre, exactly as before;
+     * s = 2..8 traces s x s samples per pixel and returns their mean.  Sample (a, b) of pixel
+     * (i, j) of a W x H screen is the reference's Trace(s i + a, s j + b, s W, s H, env).  Per
+     * channel rgb = (((+0.0 + S[0][0]) + S[0][1]) + ... + S[s-1][s-1]) / (double)(s s) (a
+     * outer, b inner, a missed sample counting as colour zero); rgb8 = uint8(255 * rgb); valid =
+     * any sample valid; face / object = those of the first valid sample in that order (-1:
+     * none); rgbv packs rgb8 and valid as usual.  max_bounces composes (every sample is a full
+     * trace).  mirt_stats counts samples: primary_rays = w h s s, the other counters summed
+     * over all samples.  Above 8: MIRT_E_INVALID; s W or s H above 65535, or more than 2^32
+     * samples in one call: MIRT_E_LIMIT.  Served by mirt_trace_tile, mirt_trace_tiles_async and
+     * mirt_box_trace_tile; mirt_trace_rays ignores it; mirt_trace_frame (frame groups) rejects
+     * s > 1 with MIRT_E_INVALID.  The samples go through a device scratch bounded by
+     * mirt_set_supersample_scratch.  DESIGN.md §4.10. */
+    uint32_t supersample;
 } mirt_frame;
 
 /* shared/comms/comms.proto:25-31 WorkOrder geometry */
@@ -356,6 +370,27 @@ int mirt_debug_light_table_gpu(mirt_ctx *ctx, const double *tri, uint32_t n, dou
  * retired), [7] the cap.
  */
 int mirt_set_light_cache(mirt_ctx *ctx, uint64_t max_bytes);
+
+/*
+ * Supersampled calls (mirt_frame.supersample = s > 1) trace their samples into a device scratch
+ * owned by the call's slot (concurrent calls never share one) and resolve them into the
+ * caller's planes with k_resolve.  A sample takes 25 bytes of scratch (rgb fp64 + valid), 33
+ * when the caller asked for face or object.  The samples a call holds at once never exceed
+ * `bytes` per context (default 256 MiB; 0: MIRT_E_INVALID): a tile whose samples exceed it is
+ * processed in bands, full-height ranges of its output columns (contiguous in the column-major
+ * planes), each traced and then resolved on the call's stream.  A band is at least one output
+ * column wide, so a single column whose samples exceed the cap is still traced, with a scratch
+ * of that column's size.  A call that needs more than one trace launch waits on the host for
+ * each launch before it stages the next (mirt_trace_tiles_async is fully asynchronous only when
+ * the call's samples fit the cap); mirt_trace_tile polls `cancel` between them.
+ * mirt_plan_supersample_bands (host only, no device): the bands of a tile list, as
+ * output-pixel rectangles in list order and left to right within a tile; with_ids != 0: face or
+ * object requested.  Returns the number of bands (writing at most cap_out of them; out may be
+ * NULL) or a negative MIRT_E_* code.
+ */
+int mirt_set_supersample_scratch(mirt_ctx *ctx, uint64_t bytes);
+int mirt_plan_supersample_bands(const mirt_tile *tiles, uint32_t n, uint32_t s, int with_ids, uint64_t cap_bytes,
+                                mirt_tile *out, uint32_t cap_out);
 int mirt_light_cache_stats(mirt_ctx *ctx, uint64_t out[8]);
 
 /*
@@ -387,7 +422,9 @@ void mirt_object_bounds(const double *v, uint32_t nv, const double pos[3], doubl
  * whole screen straight into the framebuffer (no tiles, no RCCL); world == 1 with tile > 0
  * rehearses the tiled path on one GPU.
  *   mirt_group_unique_id: rank 0 makes the RCCL id (128 bytes) every rank passes in.
- *   mirt_trace_frame:     enqueue the next frame (asynchronous; *index = its number).  Lone-frame
+ *   mirt_trace_frame:     enqueue the next frame (asynchronous; *index = its number).  A frame
+ *                         with supersample > 1 is rejected (MIRT_E_INVALID): supersampling is
+ *                         not part of the group path.  Lone-frame
  *                         hold (world == 1, tile == 0; MIRT_LONE_HOLD=0 turns it off): a batch
  *                         completed while the group has nothing running is HELD, not launched,
  *                         and runs at the next mirt_trace_frame (with the fixed grid: a burst has
@@ -499,6 +536,8 @@ int mirt_box_set_transport(mirt_box *box, int transport);
 int mirt_box_transport(const mirt_box *box);
 int mirt_box_set_strip(mirt_box *box, uint32_t strip);
 int mirt_box_set_options(mirt_box *box, uint32_t flags);
+/* mirt_set_supersample_scratch on every entry of the box. */
+int mirt_box_set_supersample_scratch(mirt_box *box, uint64_t bytes);
 int mirt_box_mesh_upload(mirt_box *box, const double *v, uint32_t nv, const double *vn, uint32_t nn,
                          const uint32_t *fv, const uint32_t *fn, const uint32_t *fmat, uint32_t nf,
                          const mirt_material *mats, uint32_t nm, uint32_t *mesh_id);

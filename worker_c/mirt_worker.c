@@ -21,8 +21,11 @@
  *              concurrently through mirt_box_trace_tile; the assembled frame must equal the
  *              one-context frame.
  *
- *   mirt_worker [--box N] <scene.json> <W> <H> <out.bin> [workers]
- *   mirt_worker [--box N] --gob <state.gob> <diff.gob> <W> <H> <out.bin> [workers]
+ *   Supersampling (--supersample N, 1..8): every BulkTrace order (and the box's) carries
+ *              mirt_frame.supersample = N; the orders and the results keep their sizes.
+ *
+ *   mirt_worker [--box N] [--supersample N] <scene.json> <W> <H> <out.bin> [workers]
+ *   mirt_worker [--box N] [--supersample N] --gob <state.gob> <diff.gob> <W> <H> <out.bin> [workers]
  * Writes rgb8 (W*H*3) then valid (W*H) of the assembled frame, column-major x*H + y.
  * Exit status 0 = every check passed.
  */
@@ -121,12 +124,20 @@ static int serve_orders(mirt_ctx *ctx, mirt_box *box, const mirt_frame *frame, c
 }
 
 int main(int argc, char **argv) {
-    int box_n = 0;
-    if (argc > 2 && strcmp(argv[1], "--box") == 0) {
-        box_n = atoi(argv[2]);
-        if (box_n < 1 || box_n > 64) {
-            fprintf(stderr, "--box needs 1..64 entries\n");
-            return 2;
+    int box_n = 0, supersample = 1;
+    while (argc > 2 && (strcmp(argv[1], "--box") == 0 || strcmp(argv[1], "--supersample") == 0)) {
+        if (strcmp(argv[1], "--box") == 0) {
+            box_n = atoi(argv[2]);
+            if (box_n < 1 || box_n > 64) {
+                fprintf(stderr, "--box needs 1..64 entries\n");
+                return 2;
+            }
+        } else {
+            supersample = atoi(argv[2]);
+            if (supersample < 1 || supersample > 8) {
+                fprintf(stderr, "--supersample needs 1..8\n");
+                return 2;
+            }
         }
         argv[2] = argv[0];  /* drop the two words: argv[0] moves up */
         argv += 2;
@@ -196,6 +207,9 @@ int main(int argc, char **argv) {
     frame.lights = lights;
     frame.n_lights = nl;
     CHECK(mirt_scene_camera(mut, &frame.camera));
+    /* --supersample N: every order returns the mean of N x N samples per pixel; the master
+     * orders and receives the same pixels (mirt.h mirt_frame.supersample) */
+    frame.supersample = (uint32_t)supersample;
 
     /* BulkTrace: the master's partition, every order on its own thread */
     rect orders[256];
@@ -212,13 +226,14 @@ int main(int argc, char **argv) {
         CHECK(mirt_trace_tile(ctx, &frame, 0, 0, W, H, W, H, &out, NULL, NULL));
     }
 
-    /* the frame group: library-owned device framebuffers, frames copied to host memory */
+    /* the frame group: library-owned device framebuffers, frames copied to host memory
+     * (frame groups do not supersample: the check runs for one ray per pixel only) */
     mirt_group *g = NULL;
     CHECK(mirt_group_create(ctx, NULL, 0, 1, W, H, 0, 0, 2, NULL, &g));
     CHECK(mirt_group_set_host_output(g, 1));
     CHECK(mirt_group_set_timeout(g, 10000));
     uint64_t idx[3];
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < 3 && supersample == 1; ++k) {
         CHECK(mirt_trace_frame(g, &frame, &idx[k]));
         if (k > 0) {
             mirt_outputs h;
