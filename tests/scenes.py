@@ -165,6 +165,39 @@ def multi_object_scene(suzanne: PyMesh) -> PyScene:
     return sc
 
 
+# limit_scene's 16-light variant that keeps colour.Add's clamp after every light under test: at
+# 0.3 the oracle's 64x48 frames have saturated and unsaturated hit pixels with 1, 3 and 16
+# objects (at 0.4 every hit pixel of the one-object scenes reaches 1.0; at 0.2 none does)
+CLAMP_LIGHT_SCALE = 0.3
+
+
+def limit_scene(n_lights: int, n_objects: int, *, big: bool = False, light_scale=None) -> PyScene:
+    """A scene at the ends of what mirt_frame allows (0..16 lights, 0..16 objects).  Meshes: a
+    sphere (vertex normals, Ns 10) and a flat-shaded cube (default material), alternating over
+    the objects; big: the sphere has 3,200 faces (more than kLdsTris).  Object 0 at the origin,
+    the others around it (seeded); the camera near (0.3, 0.4, 5) looking down -z; the lights on
+    a ring of radius about 4 around the view axis, between the camera and the objects.  Light
+    colours are uniform(0.2, 1) times light_scale (None: 0.15 with more than 5 lights, so that
+    16 of them do not saturate the frame and every single one stays visible; else 1)."""
+    rng = np.random.default_rng(100 + n_objects)  # the objects do not move with the light count
+    sc = PyScene()
+    sc.meshes = [uv_sphere(40, 40, 0.7) if big else uv_sphere(12, 24, 0.7), box_mesh(0.8)]
+    sc.objects = [(k % 2, (0.0, 0.0, 0.0) if k == 0 else tuple(float(x) for x in rng.normal(scale=1.2, size=3)))
+                  for k in range(n_objects)]
+    if light_scale is None:
+        light_scale = 0.15 if n_lights > 5 else 1.0
+    rng = np.random.default_rng(200 + n_lights)
+    phase = float(rng.uniform(0, 2 * math.pi))
+    sc.lights = []
+    for k in range(n_lights):
+        a = phase + 2 * math.pi * k / n_lights
+        r = 4.0 + float(rng.uniform(-0.3, 0.3))
+        pos = (r * math.cos(a), r * math.sin(a), 2.5 + float(rng.uniform(-0.5, 0.5)))
+        sc.lights.append((pos, tuple(float(x) * light_scale for x in rng.uniform(0.2, 1.0, 3))))
+    sc.cam_pos, sc.cam_dir, sc.fov = (0.3, 0.4, 5.0), (0.0, 0.0, -1.0), 0.9
+    return sc
+
+
 def gpu_env(ctx, sc: PyScene):
     """Upload a PyScene's meshes and build the matching EnvMutables/Environment."""
     import distributed_raytracer_amd as rt

@@ -225,6 +225,40 @@ def test_diff_camera_parallel_to_up_is_rejected():
         L.lib().mirt_scene_free(h)
 
 
+@pytest.mark.parametrize("n_lights,n_objects", [(0, 1), (16, 1), (0, 0), (16, 16)])
+def test_diff_with_no_and_sixteen_lights(n_lights, n_objects):
+    """A WorkOrder.diff at the ends of the light (and object) count, encoded here and decoded
+    by csrc/gob.cpp.  encoding/gob leaves out a struct FIELD that holds an empty slice
+    (encode.go encOpFor: "if !state.sendZero && slice.Len() == 0 { return }"; checked on a
+    struct in test_hand_built_streams), but EnvMutables.MarshalBinary passes em.Lights to
+    Encoder.Encode as a value of its own (environment.go:110), and a top-level non-struct value
+    is sent by encodeSingle with sendZero = true: an empty (or nil) []Light is the message
+    "type id, 0, count 0", which gob_go.py writes and the decoder must read as no lights."""
+    import distributed_raytracer_amd.tracer as T
+    from scenes import limit_scene
+    sc = limit_scene(n_lights, n_objects)
+    cam = (sc.cam_pos, G.norm(sc.cam_dir), sc.fov)
+    diff = G.work_order_diff([(pos, 1) for _, pos in sc.objects], sc.lights, cam)
+    # the lights' message: the last one before the camera's type definition when the slice is empty
+    empty = msg(G.enc_int(G.LSLICE.id) + b"\x00" + G.enc_uint(0))
+    assert (empty in diff) == (n_lights == 0)
+    h, _ = decode_env("example")
+    try:
+        m = C.c_void_p()
+        L.check(L.lib().mirt_scene_link_gob(h, diff, len(diff), C.byref(m)))
+        try:
+            objects, lights, got_cam = T._scene_mutables(m)
+        finally:
+            L.lib().mirt_scene_free(m)
+        assert objects == [(0, tuple(pos)) for _, pos in sc.objects]  # id 1: the example's one mesh
+        assert len(lights) == n_lights
+        assert [(lt.pos, lt.col) for lt in lights] == [(tuple(p), tuple(u8(c) / 255.0 for c in col))
+                                                       for p, col in sc.lights]
+        assert got_cam == T.Camera.new(sc.cam_pos, G.norm(sc.cam_dir), sc.fov)
+    finally:
+        L.lib().mirt_scene_free(h)
+
+
 def test_light_colour_round_trip_quantisation():
     """colour.RGB on the wire is uint8(255 c): a light of NewRGB(u8) comes back as
     NewRGB(uint8(255 (u8 / 255))), which for some u8 is u8 - 1."""
