@@ -103,3 +103,8 @@
 #ifndef MIRT_STREAM_SHADOW
 #define MIRT_STREAM_SHADOW 0
 #endif
+// k_trace: a ring chunk's lit ballots and done counter live in LDS (1) or in the device-scope
+// words of the split kernels (0: WorkArgs::litw / blkdone, two agent-scope atomics per item).
+#ifndef MIRT_CHUNK_LDS
+#define MIRT_CHUNK_LDS 1
+#endif

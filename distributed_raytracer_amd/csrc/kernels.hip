@@ -1726,6 +1726,15 @@ struct LocalChunks {
     uint32_t* ring;     // free positions of the hit-chunk ring (bit p: position p free)
     uint16_t* pos;      // per chunk: its position in the region (< kHitRing: a ring position)
     uint32_t* key;      // per chunk: its block's redo key (frame << 28 | block), redo_mark
+    uint32_t* done;     // per ring position: lights done for the chunk there (ChunkLights)
+};
+// A ring chunk's light state in LDS (k_trace; a chunk's items run in the workgroup that traced
+// its block): per ring position one lit ballot per light and the count of lights done.  Every
+// item writes its ballot, so only the count is cleared per chunk (primary_block).  Chunks
+// past the ring keep the device-scope words (WorkArgs::litw, blkdone).
+struct ChunkLights {
+    uint64_t (*lit)[MIRT_MAX_LIGHTS];
+    uint32_t* done;
 };
 
 // Hit-chunk ring (k_trace): a chunk takes the lowest free one of kHitRing positions of the
@@ -1892,8 +1901,12 @@ __device__ __forceinline__ bool primary_block(const FrameArgs& fa, const WorkArg
         } else if (!ballot) {
             st64(w + 7, at_store((uint64_t)kNoHit));
         }
-        if (is_hit || !ballot) st32(&wa.litw[slot], 0u);
-        if (lane == 0) st32(&wa.blkdone[slot / 64], 0u);
+        // a ring chunk's light state is in LDS (ChunkLights): its count is cleared below
+        const bool lds_lights = MIRT_CHUNK_LDS && lc && lc->done && rp < kHitRing;  // wave-uniform
+        if (!lds_lights) {
+            if (is_hit || !ballot) st32(&wa.litw[slot], 0u);
+            if (lane == 0) st32(&wa.blkdone[slot / 64], 0u);
+        }
         if (lc) {
             // publish to the workgroup: the chunk's stores have reached L2 (shared by every
             // wave of this CU) before its ready flag is raised in LDS
@@ -1901,6 +1914,8 @@ __device__ __forceinline__ bool primary_block(const FrameArgs& fa, const WorkArg
             __builtin_amdgcn_wave_barrier();
             if (lane == 0) {
                 lc->frame_of[base] = (uint8_t)lc->frame;  // LDS, in order before the flag
+                if (lds_lights) lc->done[rp] = 0u;        // (the position's last chunk was shaded: ring_take)
+                asm volatile("" ::: "memory");
                 __hip_atomic_store(&lc->ready[base], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
@@ -2177,8 +2192,9 @@ __device__ __forceinline__ void redo_mark(const WorkArgs& wa, uint32_t key) {
 
 // ---------------------------------------------------------------- shadow item
 // 64 hit slots (chunk c of region q) x light l: shadow rays from hit + 1e-4 L
-// (tracer.go:61-64), the lit bit published by atomicOr, and Phong (tracer.go:53-76) by
-// the wave that finishes the chunk's last light.  n_lights == 0: one pass that shades.
+// (tracer.go:61-64), the lit bit published by atomicOr (a k_trace ring chunk: the light's lit
+// ballot in LDS, cl), and Phong (tracer.go:53-76) by the wave that finishes the chunk's last
+// light.  n_lights == 0: one pass that shades.
 //   vf: the chunk's frame within the launch (its view tables, k_trace), ~0u: none.
 //   pass2 / returns: shadow_lit_single's retry.  true = the item must run again with pass2
 //   (nothing was published: no lit bit, no count, no shading); false = done.
@@ -2187,7 +2203,8 @@ __device__ __forceinline__ bool shadow_item(const FrameArgs& fa, const WorkArgs&
                                             const double* __restrict__ lds, uint32_t* __restrict__ stk, bool resident,
                                             bool segment, size_t chunk, uint32_t l, WaveStats& ws, bool pass2,
                                             uint32_t vf = ~0u, const ViewCache* vc = nullptr, uint32_t lim = 64,
-                                            uint32_t* ring = nullptr, uint32_t rpos = ~0u, uint32_t defer = ~0u) {
+                                            uint32_t* ring = nullptr, uint32_t rpos = ~0u, uint32_t defer = ~0u,
+                                            const ChunkLights* cl = nullptr) {
     // (a fresh lane index: its derived per-lane offsets are recomputed per item instead of being
     // hoisted out of the caller's item loop and held, or spilled, across every item)
     const uint32_t lane = tid_fresh<true>() & 63;
@@ -2265,16 +2282,38 @@ __device__ __forceinline__ bool shadow_item(const FrameArgs& fa, const WorkArgs&
     // atomics are coherent across XCDs and the wait orders the two atomics (the slot index is
     // recomputed here: nothing of the item's start stays live across the traversal)
     const size_t slot_b = chunk + (tid_fresh<true>() & 63);
-    if (active && is_lit) {
-        const uint32_t old =
-            __hip_atomic_fetch_or(&wa.litw[slot_b], 1u << l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("" ::"v"(old));
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // k_trace's ring chunks (ChunkLights): the light's lit ballot and the count in LDS, whose
+    // operations complete in order: no device-scope atomic and no wait on the memory counter
+    const bool lds_lights = MIRT_CHUNK_LDS && cl && ring && rpos < kHitRing;  // wave-uniform
     uint32_t done = 0;
-    if (lane == 0) done = atomicAdd(&wa.blkdone[chunk / 64], 1u);
+    if (lds_lights) {
+        const uint64_t bal = __ballot(active && is_lit);
+        if ((tid_fresh<true>() & 63) == 0) {
+            cl->lit[rpos][l] = bal;
+            asm volatile("" ::: "memory");
+            done = __hip_atomic_fetch_add(&cl->done[rpos], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    } else {
+        if (active && is_lit) {
+            const uint32_t old =
+                __hip_atomic_fetch_or(&wa.litw[slot_b], 1u << l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("" ::"v"(old));
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0) done = atomicAdd(&wa.blkdone[chunk / 64], 1u);
+    }
     done = __builtin_amdgcn_readfirstlane(done);
     if (done != nl - 1) return false;
+    // the chunk's last light: each lane's lit word from the lights' ballots (written before
+    // their counts; same-address LDS reads, one select per light)
+    uint32_t lit_l = 0;
+    if (lds_lights) {
+        asm volatile("" ::: "memory");
+        for (uint32_t k = 0; k < nl; ++k) {
+            const uint64_t b = u64_uniform(cl->lit[rpos][k]);
+            lit_l |= __builtin_amdgcn_inverse_ballot_w64(b) ? 1u << k : 0u;
+        }
+    }
     // Phong of the lane's hit (tracer.go:53-76) once its lit word is complete, and its outputs.
     // The record is read again here (hit point and obj | mat too, through a slot index the
     // compiler cannot reuse from the item's start): none of it stays live across the traversal,
@@ -2282,7 +2321,7 @@ __device__ __forceinline__ bool shadow_item(const FrameArgs& fa, const WorkArgs&
     auto shade = [&](uint64_t& oidx) {
         const size_t s2 = chunk + (tid_fresh<true>() & 63);
         const uint64_t* w2 = (const uint64_t*)&wa.hits[s2];
-        const uint32_t lit = atomicOr(&wa.litw[s2], 0u);
+        const uint32_t lit = lds_lights ? lit_l : atomicOr(&wa.litw[s2], 0u);
         const V3 h2{bitsd(ld64(w2)), bitsd(ld64(w2 + 1)), bitsd(ld64(w2 + 2))};
         const V3 n{bitsd(ld64(w2 + 3)), bitsd(ld64(w2 + 4)), bitsd(ld64(w2 + 5))};
         oidx = ld64(w2 + 6);
@@ -2764,6 +2803,9 @@ MIRT_TRACE_KERNEL void k_trace(const FrameRecs recs, const WorkArgs wa, const Fu
     __shared__ uint16_t chunk_pos[kBlkQ];  // each chunk's position in the region (ring_take)
     __shared__ uint32_t chunk_key[kBlkQ];  // each chunk's block (redo_mark)
     __shared__ uint32_t s_prim, s_pdone, s_chunks, s_item, s_front, s_back, s_ring;
+    __shared__ uint64_t ring_lit[kHitRing ? kHitRing : 1][MIRT_MAX_LIGHTS];  // ChunkLights
+    __shared__ uint32_t ring_done[kHitRing ? kHitRing : 1];
+    const ChunkLights cl{ring_lit, ring_done};
     __shared__ ViewHead s_vhead[VIEWS ? kMaxViewTables : 1];
     __shared__ uint32_t s_vstate[VIEWS ? kMaxViewTables : 1];
     const ViewCache vc{s_vhead, s_vstate};
@@ -2891,13 +2933,17 @@ MIRT_TRACE_KERNEL void k_trace(const FrameRecs recs, const WorkArgs wa, const Fu
         }
         if (threadIdx.x == 0) {
             s_prim = s_pdone = s_chunks = s_item = 0;
-            s_ring = kHitRing >= 32 ? ~0u : (1u << kHitRing) - 1u;  // every ring position free
+            // (made here: as a constant it joined s_item's zero in one 64-bit store whose
+            // register pair was hoisted out of the batch loop and spilled)
+            uint32_t every = kHitRing >= 32 ? ~0u : (1u << kHitRing) - 1u;
+            asm volatile("" : "+v"(every));
+            s_ring = every;  // every ring position free
         }
         if (c0 == 0) clock.mark_staged();
         __syncthreads();
         // queued blocks: [0, s_front) and [s_back, nc); ticket q is entry q or q - nfront + s_back
         const uint32_t nfront = s_front, back0 = s_back, nq = nfront + (nc - back0);
-        LocalChunks lc{&s_chunks, ready, chunk0, chunk_frame, 0, &s_ring, chunk_pos, chunk_key};
+        LocalChunks lc{&s_chunks, ready, chunk0, chunk_frame, 0, &s_ring, chunk_pos, chunk_key, ring_done};
         uint32_t pend = kNone;  // a shadow ticket held (possibly for a chunk not yet allocated)
         for (;;) {
             // 1. a shadow item of an allocated chunk
@@ -2922,7 +2968,7 @@ MIRT_TRACE_KERNEL void k_trace(const FrameRecs recs, const WorkArgs wa, const Fu
                 const uint32_t cp = __builtin_amdgcn_readfirstlane(chunk_pos[c]);
                 const uint32_t ck = __builtin_amdgcn_readfirstlane(chunk_key[c]);
                 shadow_item<PREFILTER, BRUTE, true, HBM1>(fr.fa, wa, fr.out, lds, stk, RESIDENT, segment, chunk0 + (size_t)cp * 64, l, wsh,
-                                              false, RESIDENT ? cf : ~0u, VIEWS ? &vc : nullptr, 64, &s_ring, cp, ck);
+                                              false, RESIDENT ? cf : ~0u, VIEWS ? &vc : nullptr, 64, &s_ring, cp, ck, &cl);
                 ic.record(wa, 1, wsh.tests - before.tests, wsh.nodes - before.nodes, 0);
                 pend = kNone;
                 continue;

@@ -1351,7 +1351,8 @@ int launch_frames(mirt_ctx* c, Slot* sl, uint32_t nf, uint32_t W, uint32_t H, co
             wa.split_redo = sl->sredo;
         }
         // the primary chunks' hit ballots (not with chains: k_reflect reads the records' obj)
-        if (!(wa.bounces && (c->flags & MIRT_OPT_REFLECT_CHAINS)) && !getenv("MIRT_NO_HIT_BALLOT")) {
+        static const bool no_hit_ballot = getenv("MIRT_NO_HIT_BALLOT") != nullptr;
+        if (!(wa.bounces && (c->flags & MIRT_OPT_REFLECT_CHAINS)) && !no_hit_ballot) {
             if ((r = dev_grow(sl->hmask, sl->hmask_cap, hit_slots / 64)) != MIRT_OK) return r;
             wa.hmask = sl->hmask;
         }
